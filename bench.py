@@ -5,7 +5,13 @@ config: Llama-3-8B bf16, synthetic random prompts of the CI benchmark
 shape (random 128-token inputs), random-init (dummy) weights, continuous
 decode at a fixed running batch.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly --steps engine steps and
+prints the result line; that is all this benchmark measures, so --full
+(reserved for measurements beyond the headline figure) adds nothing yet.
+--dump-outputs DIR writes the token ids the last timed step returned to
+its caller as DIR/new_token_ids.npy (float32, one row per request).
 
 For N>1 the driver launches this under torch.distributed.run with one
 rank per GPU; ranks form a TP=N group over RCCL/xGMI (the reference's
@@ -58,7 +64,27 @@ def parse_args():
                         "replica per rank, each with its own --batch (weak "
                         "scaling, xGMI-free — the throughput-optimal "
                         "serving layout for an 8B model)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write what the last timed step returned as "
+                        "DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none at present)")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, rank, batch, outputs):
+    """Token ids returned by one engine step, one row per request in
+    submission order (-1 where a request returned fewer tokens)."""
+    by_req = {out.req_id: out.new_token_ids for out in outputs}
+    width = max((len(t) for t in by_req.values()), default=0)
+    arr = np.full((batch, width), -1, dtype=np.float32)
+    for i in range(batch):
+        toks = by_req.get(f"r{i}", [])
+        arr[i, :len(toks)] = toks
+    os.makedirs(out_dir, exist_ok=True)
+    name = "new_token_ids" if rank == 0 else f"new_token_ids.rank{rank}"
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def main():
@@ -73,7 +99,6 @@ def main():
         args.model = "tiny-llama"
         args.dtype = "fp32"
         args.batch = min(args.batch, 8)
-        args.steps = min(args.steps, 8)
         args.block_size = 16
 
     from vllm_amd.config import (
@@ -143,12 +168,16 @@ def main():
         sync()
         t0 = time.perf_counter()
         out_tokens = 0
+        last_outputs = []
         for _ in range(args.steps):
-            for out in engine.step():
+            last_outputs = engine.step()
+            for out in last_outputs:
                 out_tokens += len(out.new_token_ids)
         sync()
         t1 = time.perf_counter()
         elapsed = t1 - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, args.batch, last_outputs)
     else:
         out_tokens = 0
         for _ in range(args.warmup):
@@ -182,7 +211,7 @@ def main():
             "n_gpus": world if on_gpu else 0,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1000, 3),
+            "ms_per_step": round(elapsed / max(args.steps, 1) * 1000, 3),
             "higher_is_better": True,
             "scaling": "weak" if dp_mode else "strong",
             "vs_baseline": None,

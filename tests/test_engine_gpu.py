@@ -192,20 +192,43 @@ def test_gemma3_gpu_decode():
 
 def test_medusa_gpu_matches_baseline():
     """Medusa drafts on GPU (incl. the hipGraph hidden capture) must not
-    change greedy output vs the non-speculative run."""
+    change greedy output vs the non-speculative run.
+
+    Greedy output is only defined where the argmax is unique: the
+    periodic first prompt drives the tiny random model into an exact tie
+    of two bf16 logits (baseline top-2 logprob gap 0.0 at its 5th
+    token), and the decode and verify kernels may break that tie either
+    way. So the runs must agree token for token up to a position where
+    the baseline itself scores both choices exactly equal (zero
+    tolerance); past such a tie the two continuations are different
+    sequences and are not compared."""
     from vllm_amd.sampling_params import SamplingParams
 
     prompts = [[7, 8, 9, 10] * 10, list(range(50, 90))]
     p = SamplingParams(temperature=0.0, max_tokens=16, ignore_eos=True)
     llm = _llm()
-    base = [o.outputs[0].token_ids for o in llm.generate(prompts, p)]
+    base_out = llm.generate(
+        prompts, SamplingParams(temperature=0.0, max_tokens=16,
+                                ignore_eos=True, logprobs=4))
     llm.shutdown()
     llm = _llm(num_speculative_tokens=3, spec_decode_method="medusa")
     med = [o.outputs[0].token_ids for o in llm.generate(prompts, p)]
     sched = llm.engine.engine_core.scheduler
     assert sched.spec_stats_drafted > 0
     llm.shutdown()
-    assert base == med
+    whole = 0
+    for o, m in zip(base_out, med):
+        b, lps = o.outputs[0].token_ids, o.outputs[0].logprobs
+        assert len(b) == len(m) == 16
+        if b == m:
+            whole += 1
+            continue
+        i = next(j for j in range(16) if b[j] != m[j])
+        assert i > 0, (b, m)
+        assert m[i] in lps[i], (i, b, m, lps[i])
+        assert lps[i][m[i]] == lps[i][b[i]], (i, b, m, lps[i])
+    # A tie is the exception: at least one prompt matches in full.
+    assert whole >= 1
 
 
 def test_sleep_wake_gpu():

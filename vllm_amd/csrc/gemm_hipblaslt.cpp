@@ -18,6 +18,7 @@
 #include <hipblaslt/hipblaslt-ext.hpp>
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <unordered_map>
@@ -78,7 +79,8 @@ uint64_t shape_key(int64_t m, int64_t n, int64_t k, bool bf16, bool bias) {
 // matmulIsAlgoSupported) — the heuristic alone left ~40% on the table
 // for the decode-shape GEMMs (profiles/r01_summary.md). Two-phase race:
 // one timed rep over every supported candidate, then a longer rerace of
-// the top finishers. VLLM_AMD_GEMM_TUNE=quick restores heuristic-only.
+// the top finishers, each phase within a wall-clock budget (below).
+// VLLM_AMD_GEMM_TUNE=quick restores heuristic-only.
 template <typename Call>
 hipblasLtMatmulAlgo_t pick_algo(uint64_t key, hipblasLtMatmulDesc_t op_desc,
                                 hipblasLtMatrixLayout_t lw,
@@ -141,18 +143,40 @@ hipblasLtMatmulAlgo_t pick_algo(uint64_t key, hipblasLtMatmulDesc_t op_desc,
     HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
     return ms;
   };
-  // Phase A: one rep each over the whole pool.
+  // Each phase has a wall-clock budget so that the race costs a bounded
+  // time per shape. Decode-size GEMMs (tens of microseconds a call)
+  // finish the whole pool far inside it; a prefill GEMM of tens of
+  // milliseconds stops after the heuristic's leading candidates, where
+  // one rep is already a stable measurement.
+  // VLLM_AMD_GEMM_TUNE=exhaustive lifts the budget.
+  const bool budgeted = tune == nullptr || strcmp(tune, "exhaustive") != 0;
+  constexpr double kPhaseABudgetMs = 600.0, kPhaseBBudgetMs = 300.0;
+  constexpr int kMinPhaseA = 4;
+  using clock = std::chrono::steady_clock;
+  auto elapsed_ms = [](clock::time_point since) {
+    return std::chrono::duration<double, std::milli>(clock::now() - since)
+        .count();
+  };
+  // Phase A: one rep each over the pool (heuristic's picks come first).
   std::vector<std::pair<float, int>> ranked;
   ranked.reserve(results.size());
-  for (int i = 0; i < (int)results.size(); ++i)
+  auto phase_start = clock::now();
+  for (int i = 0; i < (int)results.size(); ++i) {
+    if (budgeted && i >= kMinPhaseA &&
+        elapsed_ms(phase_start) > kPhaseABudgetMs)
+      break;
     ranked.emplace_back(time_algo(results[i].algo, 1), i);
+  }
   std::sort(ranked.begin(), ranked.end(),
             [](auto& x, auto& y) { return x.first < y.first; });
   // Phase B: rerace the 12 fastest with more reps.
   float best = 1e30f;
   int best_i = ranked[0].second;
+  phase_start = clock::now();
   for (int j = 0; j < std::min<int>(12, (int)ranked.size()); ++j) {
     if (ranked[j].first >= 1e30f) break;
+    if (budgeted && j >= 1 && elapsed_ms(phase_start) > kPhaseBBudgetMs)
+      break;
     const int i = ranked[j].second;
     const float ms = time_algo(results[i].algo, 8);
     if (ms < best) {

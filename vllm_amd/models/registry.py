@@ -77,7 +77,7 @@ def initialize_dummy_weights(model: torch.nn.Module, seed: int = 0) -> None:
         gen = torch.Generator()
         gen.manual_seed(seed ^ zlib.crc32(name.encode()))
         cpu_val = torch.rand(shape, generator=gen,
-                             dtype=torch.float32) * 2.0 - 1.0
+                             dtype=torch.float32).mul_(2.0).sub_(1.0)
         # Scales chosen so the network is a FUNCTIONING transformer, not
         # a constant map: norm gains at ~1 and matrices at 1/sqrt(fan_in)
         # keep activations O(1) through deep stacks (RMSNorm re-centers
@@ -91,8 +91,13 @@ def initialize_dummy_weights(model: torch.nn.Module, seed: int = 0) -> None:
         fan_in = shape[-1] if len(shape) >= 2 else 1
         if len(shape) > 2 and "patch" in name.lower():
             fan_in = int(torch.tensor(shape[1:]).prod())
-        return cpu_val / math.sqrt(fan_in)
+        return cpu_val.div_(math.sqrt(fan_in))
 
+    # (numel, name, full shape, param, shard fn) per distinct parameter.
+    # The CPU generator is serial, and every parameter has its own, so
+    # the parameters are filled on a thread pool (largest first): the
+    # values do not depend on the order or the number of threads.
+    jobs = []
     handled: set[int] = set()
     for mod_name, mod in model.named_modules():
         shapes_fn = getattr(mod, "dummy_shard_shapes", None)
@@ -103,15 +108,30 @@ def initialize_dummy_weights(model: torch.nn.Module, seed: int = 0) -> None:
             if param is None or id(param) in handled:
                 continue
             gname = f"{mod_name}.{pname}" if mod_name else pname
-            full = gen_full(gname, tuple(full_shape))
-            param.data.copy_(
-                mod.dummy_shard(pname, full).to(param.dtype))
+            shard = (lambda full, mod=mod, pname=pname:
+                     mod.dummy_shard(pname, full))
+            jobs.append((math.prod(full_shape), gname, tuple(full_shape),
+                         param, shard))
             handled.add(id(param))
     for name, param in model.named_parameters():
         if id(param) in handled:
             continue
-        val = gen_full(name, tuple(param.shape))
+        handled.add(id(param))
+        jobs.append((param.numel(), name, tuple(param.shape), param, None))
+
+    def fill(job) -> None:
+        _, name, shape, param, shard = job
+        val = gen_full(name, shape)
+        if shard is not None:
+            val = shard(val)
         param.data.copy_(val.to(param.dtype))
+
+    jobs.sort(key=lambda j: -j[0])
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max_workers=max(1, torch.get_num_threads())) \
+            as pool:
+        list(pool.map(fill, jobs))
 
 
 def load_model(config: ModelConfig, device: torch.device) -> torch.nn.Module:

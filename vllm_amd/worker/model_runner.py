@@ -175,6 +175,14 @@ class DecodeGraphRunner:
             runner.model.compute_logits(hidden)
         torch.cuda.current_stream().wait_stream(s)
         graph = torch.cuda.CUDAGraph()
+        # The first graph to register with the default generator allocates
+        # the generator's capture-state tensors. Steps run in inference
+        # mode; tensors allocated there could not be updated by a later
+        # capture outside it (anywhere in the process), so register here
+        # with inference mode off.
+        with torch.inference_mode(False):
+            graph.register_generator_state(
+                torch.cuda.default_generators[torch.cuda.current_device()])
         with torch.cuda.graph(graph, pool=self.pool), set_forward_context(ctx):
             hidden = runner.model(self.input_ids[:nb], self.positions[:nb])
             logits = runner.model.compute_logits(hidden)
