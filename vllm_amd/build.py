@@ -26,6 +26,7 @@ SOURCES = [
     CSRC / "moe.hip",
     CSRC / "mla.hip",
     CSRC / "quant_fp8.hip",
+    CSRC / "gemm_w4a16.hip",
     CSRC / "attention_decode.hip",
     CSRC / "attention_prefill.hip",
     CSRC / "gemm_hipblaslt.cpp",

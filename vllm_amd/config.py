@@ -1187,6 +1187,9 @@ class ModelConfig:
     # "fp8": W8A8 e4m3 — per-channel weight scales (quantized after
     # load), per-token dynamic activation scales, fp8 MFMA GEMMs. Dense
     # linears only; lm_head and MoE expert weights stay in model dtype.
+    # "int4": W4A16 — 4-bit codes, bf16 scale + integer zero-point per
+    # 128-wide K group (quantized after load), bf16 activations, native
+    # dequant-GEMM (csrc/gemm_w4a16.hip). Same module selection as fp8.
     quantization: Optional[str] = None
     spec: ModelSpec = None  # type: ignore[assignment]
 
@@ -1197,13 +1200,13 @@ class ModelConfig:
             self.max_model_len, self.spec.max_position_embeddings
         )
         if self.quantization is not None:
-            if self.quantization != "fp8":
+            if self.quantization not in ("fp8", "int4"):
                 raise ValueError(
                     f"unsupported quantization {self.quantization!r}")
             if self.dtype not in ("bf16", "fp32"):
                 raise ValueError(
-                    "quantization=fp8 requires dtype bf16 (GPU) or fp32 "
-                    "(CPU simulation)")
+                    f"quantization={self.quantization} requires dtype "
+                    "bf16 (GPU) or fp32 (CPU simulation)")
 
     @property
     def torch_dtype(self) -> torch.dtype:

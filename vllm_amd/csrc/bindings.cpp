@@ -38,6 +38,9 @@ void dynamic_quant_fp8(torch::Tensor out, torch::Tensor scales,
 void scale_rows_cols(torch::Tensor y, torch::Tensor row_scales,
                      torch::Tensor col_scales,
                      c10::optional<torch::Tensor> bias);
+torch::Tensor w4a16_gemm(torch::Tensor x, torch::Tensor qweight,
+                         torch::Tensor scales, torch::Tensor zeros,
+                         c10::optional<torch::Tensor> bias);
 void moe_align(torch::Tensor topk_ids, int64_t num_experts,
                torch::Tensor sorted, torch::Tensor expert_tiles,
                torch::Tensor inv_perm, torch::Tensor counts,
@@ -90,6 +93,8 @@ TORCH_LIBRARY(vllm_amd, m) {
         " -> ()");
   m.def("scale_rows_cols(Tensor(a!) y, Tensor row_scales, Tensor col_scales,"
         " Tensor? bias) -> ()");
+  m.def("w4a16_gemm(Tensor x, Tensor qweight, Tensor scales, Tensor zeros, "
+        "Tensor? bias) -> Tensor");
   m.def("moe_align(Tensor topk_ids, int num_experts, Tensor(a!) sorted, "
         "Tensor(b!) expert_tiles, Tensor(c!) inv_perm, Tensor(d!) counts, "
         "Tensor(e!) fill, Tensor(f!) off) -> ()");
@@ -136,6 +141,7 @@ TORCH_LIBRARY_IMPL(vllm_amd, CUDA, m) {
   m.impl("lt_linear_fp8", &vllm_amd::lt_linear_fp8);
   m.impl("dynamic_quant_fp8", &vllm_amd::dynamic_quant_fp8);
   m.impl("scale_rows_cols", &vllm_amd::scale_rows_cols);
+  m.impl("w4a16_gemm", &vllm_amd::w4a16_gemm);
   m.impl("car_all_reduce", &vllm_amd::car_all_reduce);
   m.impl("car_all_gather", &vllm_amd::car_all_gather);
   m.impl("car_reduce_scatter", &vllm_amd::car_reduce_scatter);

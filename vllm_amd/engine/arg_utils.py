@@ -77,7 +77,7 @@ class EngineArgs:
         parser.add_argument("--seed", type=int, default=0)
         parser.add_argument("--enforce-eager", action="store_true")
         parser.add_argument("--quantization", "-q", type=str,
-                            default=None, choices=["fp8"])
+                            default=None, choices=["fp8", "int4"])
         parser.add_argument("--block-size", type=int, default=16)
         parser.add_argument("--gpu-memory-utilization", type=float,
                             default=0.90)

@@ -27,11 +27,16 @@ from vllm_amd.parallel.state import (
 
 
 def _run_gemm(module, x, bias):
-    """Dispatch to the fp8 W8A8 path when this layer has been quantized
-    (registry.quantize_model_fp8), else the bf16/fp16 tuned GEMM."""
+    """Dispatch to the fp8 W8A8 or int4 W4A16 path when this layer has
+    been quantized (registry.quantize_model_fp8 / quantize_model_int4),
+    else the bf16/fp16 tuned GEMM."""
     w8 = getattr(module, "weight_fp8", None)
     if w8 is not None:
         return ops.linear_fp8(x, w8, module.weight_scale, bias)
+    w4 = getattr(module, "weight_int4", None)
+    if w4 is not None:
+        return ops.linear_int4(x, w4, module.weight_scale,
+                               module.weight_zero, bias)
     return ops.linear(x, module.weight, bias)
 
 
@@ -41,6 +46,20 @@ def _quantize_fp8(module):
     w8, scale = ops.quantize_weight_fp8(module.weight.data)
     module.register_buffer("weight_fp8", w8)
     module.register_buffer("weight_scale", scale)
+    module.weight.data = module.weight.data.new_empty(0)
+
+
+def _quantize_int4(module):
+    """Convert this layer's weight to packed 4-bit codes + per-group
+    scales/zero-points and free the wide copy (0.53 B per weight). A
+    shape the W4A16 kernel cannot tile stays in model dtype."""
+    n, k = module.weight.shape
+    if k % 128 != 0 or n % 16 != 0:
+        return
+    q, scale, zero = ops.quantize_weight_int4(module.weight.data)
+    module.register_buffer("weight_int4", q)
+    module.register_buffer("weight_scale", scale)
+    module.register_buffer("weight_zero", zero)
     module.weight.data = module.weight.data.new_empty(0)
 
 
@@ -84,6 +103,7 @@ class ReplicatedLinear(nn.Module):
         return _run_gemm(self, x, self.bias)
 
     quantize_fp8 = _quantize_fp8
+    quantize_int4 = _quantize_int4
 
 
 class ColumnParallelLinear(nn.Module):
@@ -127,6 +147,7 @@ class ColumnParallelLinear(nn.Module):
         return y
 
     quantize_fp8 = _quantize_fp8
+    quantize_int4 = _quantize_int4
 
     def load_weight(self, full_weight: torch.Tensor) -> None:
         tp, rank = get_tp_world_size(), get_tp_rank()
@@ -315,3 +336,4 @@ class RowParallelLinear(nn.Module):
         return full.chunk(tp, dim=1)[rank]
 
     quantize_fp8 = _quantize_fp8
+    quantize_int4 = _quantize_int4

@@ -152,6 +152,8 @@ def load_model(config: ModelConfig, device: torch.device) -> torch.nn.Module:
     model = model.to(device).eval()
     if config.quantization == "fp8":
         quantize_model_fp8(model)
+    elif config.quantization == "int4":
+        quantize_model_int4(model)
     return model
 
 
@@ -171,3 +173,21 @@ def quantize_model_fp8(model: torch.nn.Module) -> None:
         if isinstance(module, (ColumnParallelLinear, RowParallelLinear,
                                ReplicatedLinear)):
             module.quantize_fp8()
+
+
+def quantize_model_int4(model: torch.nn.Module) -> None:
+    """Quantize every dense linear to W4A16 after load and after TP
+    sharding (4-bit codes, bf16 scale + zero-point per 128-wide K group).
+    Same module selection as quantize_model_fp8: lm_head, embedding and
+    MoE experts stay in model dtype. A layer whose local shape the kernel
+    cannot tile (K % 128, N % 16) is left in model dtype."""
+    from vllm_amd.layers.linear import (
+        ColumnParallelLinear,
+        ReplicatedLinear,
+        RowParallelLinear,
+    )
+
+    for module in model.modules():
+        if isinstance(module, (ColumnParallelLinear, RowParallelLinear,
+                               ReplicatedLinear)):
+            module.quantize_int4()

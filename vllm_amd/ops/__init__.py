@@ -124,6 +124,14 @@ def quant_fp8_dynamic(x):
 
 # Weight quantization happens once at load — plain torch either device.
 from vllm_amd.ops._torch_ref import quantize_weight_fp8  # noqa: E402,F401
+from vllm_amd.ops._torch_ref import quantize_weight_int4  # noqa: E402,F401
+
+
+def linear_int4(x, qweight, scales, zeros, bias=None):
+    """W4A16 linear: 4-bit group-quantized weights (quantize_weight_int4),
+    bf16 activations. Hand-written dequant-GEMM on GPU
+    (csrc/gemm_w4a16.hip); dequantize + fp32 F.linear on CPU."""
+    return get_backend(x.device).linear_int4(x, qweight, scales, zeros, bias)
 
 
 def concat_and_cache_mla(c_kv, k_pe, kv_cache, slot_mapping):

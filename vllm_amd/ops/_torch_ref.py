@@ -183,6 +183,79 @@ def linear_fp8(x, w_fp8, w_scale, bias=None):
     return y.to(x.dtype).reshape(shape)
 
 
+INT4_GROUP = 128  # K values per (scale, zero) pair == one 16 B lane load
+
+# Nibble position of fragment element e inside its int32 (see
+# csrc/gemm_w4a16.hip): even elements in the low half-word, odd in the
+# high, so one shift+mask yields a bf16 pair.
+_INT4_NIBBLE_SHIFT = [4 * ((e >> 1) + 4 * (e & 1)) for e in range(8)]
+
+
+def pack_weight_int4(q, scales, zeros):
+    """Lay out codes q [N, K] (0..15), scales [N, K/128] and integer
+    zero-points [N, K/128] (0..15) in the W4A16 kernel's consumer order:
+    qweight int32 [N/16, K/128, 64, 4], scales bf16 / zeros uint8
+    [N/16, K/128, 16]. Lane = (k%32//8)*16 + n%16, word = k%128//32,
+    element = k%8."""
+    N, K = q.shape
+    G = K // INT4_GROUP
+    assert K % INT4_GROUP == 0 and N % 16 == 0, (N, K)
+    # [nt, col, g, word j, l4, elem e] -> [nt, g, l4, col, j, e]
+    v = q.to(torch.int64).view(N // 16, 16, G, 4, 4, 8)
+    v = v.permute(0, 2, 4, 1, 3, 5)
+    shift = torch.tensor(_INT4_NIBBLE_SHIFT, dtype=torch.int64,
+                         device=q.device)
+    word = (v << shift).sum(dim=-1)
+    word = torch.where(word >= 2 ** 31, word - 2 ** 32, word)
+    qweight = word.to(torch.int32).reshape(N // 16, G, 64, 4).contiguous()
+
+    def tile(t, dtype):
+        return t.view(N // 16, 16, G).permute(0, 2, 1).to(dtype).contiguous()
+
+    return qweight, tile(scales, torch.bfloat16), tile(zeros, torch.uint8)
+
+
+def quantize_weight_int4(w, group_size=INT4_GROUP):
+    """Asymmetric 4-bit group quantization (done once at load, AWQ's
+    arithmetic): per (row, 128-wide K group) a bf16 scale s and an
+    integer zero-point z with w ~ (q - z) * s, q in 0..15. The min/max
+    range is widened to contain 0 so z lands in 0..15; s is rounded to
+    bf16 first and q, z are computed against the stored s.
+
+    w: [N, K] -> (qweight, scales, zeros) as laid out by pack_weight_int4."""
+    assert group_size == INT4_GROUP, "the W4A16 kernel fixes group_size=128"
+    N, K = w.shape
+    wf = w.float().view(N, K // group_size, group_size)
+    lo = wf.amin(dim=-1).clamp(max=0.0)
+    hi = wf.amax(dim=-1).clamp(min=0.0)
+    s = ((hi - lo) / 15.0).clamp_min(1e-30).to(torch.bfloat16)
+    sf = s.float()
+    z = torch.round(-lo / sf).clamp(0, 15)
+    q = (torch.round(wf / sf.unsqueeze(-1)) + z.unsqueeze(-1)).clamp(0, 15)
+    return pack_weight_int4(q.view(N, K), s, z)
+
+
+def dequantize_weight_int4(qweight, scales, zeros):
+    """Exact inverse of pack_weight_int4: fp32 [N, K] of (q - z) * s.
+    Ground truth for the W4A16 kernel and the body of the CPU path."""
+    NT, G = qweight.shape[:2]
+    shift = torch.tensor(_INT4_NIBBLE_SHIFT, dtype=torch.int64,
+                         device=qweight.device)
+    word = qweight.to(torch.int64).view(NT, G, 4, 16, 4, 1)
+    q = ((word >> shift) & 0xF).float()  # [nt, g, l4, col, j, e]
+    s = scales.float().view(NT, G, 1, 16, 1, 1)
+    z = zeros.float().view(NT, G, 1, 16, 1, 1)
+    w = (q - z) * s
+    return w.permute(0, 3, 1, 4, 2, 5).reshape(NT * 16, G * INT4_GROUP)
+
+
+def linear_int4(x, qweight, scales, zeros, bias=None):
+    """W4A16 linear, CPU reference: dequantize, then F.linear in fp32."""
+    w = dequantize_weight_int4(qweight, scales, zeros)
+    y = F.linear(x.float(), w, None if bias is None else bias.float())
+    return y.to(x.dtype)
+
+
 def topk_softmax(gating_logits, topk, renormalize=True):
     """gating_logits: [T, E] -> (topk_weights [T,k] f32, topk_ids [T,k] i32)."""
     probs = gating_logits.float().softmax(dim=-1)

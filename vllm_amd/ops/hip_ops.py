@@ -77,6 +77,17 @@ def linear_fp8(x, w_fp8, w_scale, bias=None):
     return y.reshape(shape)
 
 
+def linear_int4(x, qweight, scales, zeros, bias=None):
+    """W4A16 linear (csrc/gemm_w4a16.hip): packed 4-bit codes streamed
+    from HBM and dequantized in registers into the MFMA B operand; bf16
+    activations and output. One launch, no workspace, no host sync."""
+    shape = list(x.shape)
+    x2 = x.reshape(-1, shape[-1]).contiguous()
+    y = _C.w4a16_gemm(x2, qweight, scales, zeros, bias)
+    shape[-1] = qweight.shape[0] * 16
+    return y.reshape(shape)
+
+
 def reshape_and_cache(key, value, kv_cache, slot_mapping):
     _C.reshape_and_cache(key, value, kv_cache, slot_mapping)
 

@@ -4,8 +4,13 @@ Role of the reference's layers/quantization/awq.py checkpoint handling:
 AWQ (4-bit, group-scaled, zero-pointed) checkpoints are DEQUANTIZED at
 load into the model dtype, so any AWQ-packed model runs today; combining
 with `--quantization fp8` re-quantizes the dequantized weights to W8A8
-for the fp8 MFMA path. A native int4 dequant-GEMM kernel (keeping the 4×
-weight-memory saving at run time) is a tracked round-2 item.
+for the fp8 MFMA path, and combining with `--quantization int4`
+re-quantizes them group-wise (128 along K, after TP sharding) for the
+native W4A16 dequant-GEMM (csrc/gemm_w4a16.hip), which keeps the 4-bit
+footprint at run time. That re-quantization starts from the dequantized
+values, so it is close to but not bit-identical with the checkpoint's
+own codes; a direct repack of qweight/qzeros/scales through the TP
+loaders is a follow-up.
 
 AWQ packing: qweight int32 [K, N/8] — eight 4-bit values per int32
 along the OUTPUT dim in the interleaved order [0, 2, 4, 6, 1, 3, 5, 7];

@@ -636,10 +636,10 @@ class ModelRunner:
         from vllm_amd.models.weight_loader import load_safetensors_weights
 
         mc = self.config.model_config
-        if mc.quantization == "fp8":
+        if mc.quantization in ("fp8", "int4"):
             raise ValueError(
-                "update_weights into fp8-quantized layers needs "
-                "requantization — reload instead (sleep(2)/wake_up)")
+                f"update_weights into {mc.quantization}-quantized layers "
+                "needs requantization — reload instead (sleep(2)/wake_up)")
         cfg = dataclasses.replace(mc, model_path=model_path,
                                   load_format="safetensors")
         load_safetensors_weights(self.model, cfg)
