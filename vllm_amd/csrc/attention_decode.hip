@@ -60,7 +60,34 @@ __global__ __launch_bounds__(DEC_BLOCK) void paged_decode_kernel(
   const int seq = blockIdx.x;       // decode row == request row
   const int kvh = blockIdx.y;
   const int part = blockIdx.z;
+
+  constexpr int LPT = HD / 8;                   // lanes per token
+  constexpr int SLOTS_PER_WAVE = WAVE_SIZE / LPT;
+  constexpr int SLOTS = DEC_BLOCK / LPT;
+  const int lane_d = threadIdx.x & (LPT - 1);   // dim-slice owner
+  const int slot = (threadIdx.x / LPT) % SLOTS_PER_WAVE;
+  const int wave = threadIdx.x / WAVE_SIZE;     // 0..3
+  const int hq0 = kvh * GROUP;  // first query head of this group
+
+  // Prologue loads, issued together: none of these addresses depends on
+  // ctx, so seq_lens, the block-table entries and the q fragment share one
+  // memory round trip. Block-table columns are clamped to the request's
+  // row (entries past ceil(ctx/64) are never dereferenced).
   const int ctx = seq_lens[seq];
+  int my_blk = 0;
+  if (threadIdx.x < DEC_PART / 64) {
+    const int cache_blk = min((part * DEC_PART) / 64 + (int)threadIdx.x,
+                              max_blocks_per_req - 1);
+    my_blk = block_table[(int64_t)seq * max_blocks_per_req + cache_blk];
+  }
+  s16x8 q_raw[GROUP];
+  {
+    const short* qbase =
+        q + (int64_t)seq * q_stride + hq0 * head_dim + lane_d * 8;
+#pragma unroll
+    for (int g = 0; g < GROUP; ++g)
+      q_raw[g] = *reinterpret_cast<const s16x8*>(qbase + g * head_dim);
+  }
 
   int t_begin = part * DEC_PART;
   int t_end = min(ctx, t_begin + DEC_PART);
@@ -68,8 +95,6 @@ __global__ __launch_bounds__(DEC_BLOCK) void paged_decode_kernel(
     // Query position is ctx-1; keys < ctx - sliding_window are masked.
     t_begin = max(t_begin, ctx - sliding_window);
   }
-  const int hq0 = kvh * GROUP;  // first query head of this group
-
   if (t_begin >= t_end) {
     if (!FINAL && threadIdx.x < GROUP * 2) {
       const int g = threadIdx.x / 2;
@@ -80,43 +105,55 @@ __global__ __launch_bounds__(DEC_BLOCK) void paged_decode_kernel(
     return;
   }
 
-  constexpr int LPT = HD / 8;                   // lanes per token
-  constexpr int SLOTS_PER_WAVE = WAVE_SIZE / LPT;
-  constexpr int SLOTS = DEC_BLOCK / LPT;
-  const int lane_d = threadIdx.x & (LPT - 1);   // dim-slice owner
-  const int slot = (threadIdx.x / LPT) % SLOTS_PER_WAVE;
-  const int wave = threadIdx.x / WAVE_SIZE;     // 0..3
-
   // LDS: physical block ids + cross-wave merge scratch.
   __shared__ int blk_ids[DEC_PART / 64];
   __shared__ float ml_red[4][GROUP][2];       // per-wave (m, l)
   __shared__ float o_red[4][GROUP][HD];       // per-wave accumulators
 
-  if (threadIdx.x < DEC_PART / 64) {
-    const int cache_blk = (part * DEC_PART) / 64 + threadIdx.x;
-    blk_ids[threadIdx.x] =
-        block_table[(int64_t)seq * max_blocks_per_req + cache_blk];
-  }
+  if (threadIdx.x < DEC_PART / 64) blk_ids[threadIdx.x] = my_blk;
   __syncthreads();
+
+  using CT = CacheTraits<CTag>;
+  using cvec = typename CT::vec8;
+  const int64_t head_tile_stride = (int64_t)64 * head_dim;  // one (blk,head)
+  // Raw K/V loads of one loop trip for the slot's tokens t and t + SLOTS
+  // (t < t_end). A missing second token re-reads the first one's rows.
+  auto load_trip = [&](const int t, cvec& k0, cvec& v0, cvec& k1, cvec& v1) {
+    const int t1 = t + SLOTS;
+    const bool has1 = t1 < t_end;
+    const int local0 = t - part * DEC_PART;
+    const typename CT::elem* base0 = kv_cache +
+        ((int64_t)blk_ids[local0 / 64] * num_kv_heads + kvh) *
+            head_tile_stride +
+        (int64_t)(t % 64) * head_dim + lane_d * 8;
+    const int local1 = has1 ? t1 - part * DEC_PART : local0;
+    const typename CT::elem* base1 = has1 ? kv_cache +
+        ((int64_t)blk_ids[local1 / 64] * num_kv_heads + kvh) *
+            head_tile_stride +
+        (int64_t)(t1 % 64) * head_dim + lane_d * 8 : base0;
+    k0 = *reinterpret_cast<const cvec*>(base0);
+    v0 = *reinterpret_cast<const cvec*>(base0 + kv_plane_stride);
+    k1 = *reinterpret_cast<const cvec*>(base1);
+    v1 = *reinterpret_cast<const cvec*>(base1 + kv_plane_stride);
+  };
+
+  // First trip's K/V go out before the q fragment is converted.
+  const int t0_base = t_begin + wave * SLOTS_PER_WAVE + slot;
+  cvec nk0 = {}, nv0 = {}, nk1 = {}, nv1 = {};
+  if (t0_base < t_end) load_trip(t0_base, nk0, nv0, nk1, nv1);
 
   // Q fragment: each lane16 holds its 8-dim slice for all GROUP heads.
   float qf[GROUP][8];
-  {
-    const short* qbase =
-        q + (int64_t)seq * q_stride + hq0 * head_dim + lane_d * 8;
 #pragma unroll
-    for (int g = 0; g < GROUP; ++g) {
-      s16x8 v = *reinterpret_cast<const s16x8*>(qbase + g * head_dim);
+  for (int g = 0; g < GROUP; ++g) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) qf[g][j] = to_f32<Tag>(v[j]) * scale;
-    }
+    for (int j = 0; j < 8; ++j) qf[g][j] = to_f32<Tag>(q_raw[g][j]) * scale;
   }
 
   // ---- single pass: online softmax per (wave, slot) ----------------------
   // Each slot streams tokens t = t_begin + wave*4 + slot + 16*i. K and V
   // rows are read once, 16 B per lane (G13); no syncthreads in the loop, so
   // the 4 waves keep the HBM pipeline full independently.
-  const int64_t head_tile_stride = (int64_t)64 * head_dim;  // one (blk,head)
   float m_s[GROUP], l_s[GROUP], acc[GROUP][8];
 #pragma unroll
   for (int g = 0; g < GROUP; ++g) {
@@ -128,26 +165,15 @@ __global__ __launch_bounds__(DEC_BLOCK) void paged_decode_kernel(
 
   // Two tokens per (wave, slot) iteration: doubles the K/V loads in
   // flight per lane and halves the online-softmax update chain.
-  const int t0_base = t_begin + wave * SLOTS_PER_WAVE + slot;
+  // Pipelined one trip deep: trip i+1's raw K/V loads are issued before
+  // trip i's arithmetic and converted to fp32 only when consumed. Past the
+  // last trip the prefetch is clamped to the current token's rows, so it
+  // never leaves the request's blocks.
   for (int t = t0_base; t < t_end; t += 2 * SLOTS) {
-    const int t1 = t + SLOTS;
-    const bool has1 = t1 < t_end;
-    using CT = CacheTraits<CTag>;
-    using cvec = typename CT::vec8;
-    const int local0 = t - part * DEC_PART;
-    const typename CT::elem* base0 = kv_cache +
-        ((int64_t)blk_ids[local0 / 64] * num_kv_heads + kvh) *
-            head_tile_stride +
-        (int64_t)(t % 64) * head_dim + lane_d * 8;
-    const int local1 = has1 ? t1 - part * DEC_PART : local0;
-    const typename CT::elem* base1 = has1 ? kv_cache +
-        ((int64_t)blk_ids[local1 / 64] * num_kv_heads + kvh) *
-            head_tile_stride +
-        (int64_t)(t1 % 64) * head_dim + lane_d * 8 : base0;
-    cvec k0 = *reinterpret_cast<const cvec*>(base0);
-    cvec v0 = *reinterpret_cast<const cvec*>(base0 + kv_plane_stride);
-    cvec k1 = *reinterpret_cast<const cvec*>(base1);
-    cvec v1 = *reinterpret_cast<const cvec*>(base1 + kv_plane_stride);
+    const bool has1 = t + SLOTS < t_end;
+    const cvec k0 = nk0, v0 = nv0, k1 = nk1, v1 = nv1;
+    const int t_next = t + 2 * SLOTS;
+    load_trip(t_next < t_end ? t_next : t, nk0, nv0, nk1, nv1);
     float kf0[8], vf0[8], kf1[8], vf1[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -313,6 +339,7 @@ void paged_decode_attention(torch::Tensor out, torch::Tensor q,
   const int num_parts =
       (int)((max_seq_len + DEC_PART - 1) / DEC_PART);
   const int max_blocks = block_table.size(1);
+  TORCH_CHECK(max_blocks >= 1, "block_table has no columns");
   auto stream = c10::hip::getCurrentHIPStream().stream();
 
   dim3 grid(num_seqs, num_kv_heads, num_parts);

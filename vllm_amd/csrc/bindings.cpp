@@ -19,6 +19,9 @@ void rotary_embedding(torch::Tensor positions, torch::Tensor q,
                       int64_t rot);
 void reshape_and_cache(torch::Tensor key, torch::Tensor value,
                        torch::Tensor kv_cache, torch::Tensor slot_mapping);
+void rope_and_cache(torch::Tensor positions, torch::Tensor q, torch::Tensor k,
+                    torch::Tensor v, torch::Tensor cos_sin_cache, int64_t rot,
+                    torch::Tensor kv_cache, torch::Tensor slot_mapping);
 void paged_decode_attention(torch::Tensor out, torch::Tensor q,
                             torch::Tensor kv_cache,
                             torch::Tensor block_table,
@@ -80,6 +83,9 @@ TORCH_LIBRARY(vllm_amd, m) {
         "Tensor cos_sin_cache, int rot) -> ()");
   m.def("reshape_and_cache(Tensor key, Tensor value, Tensor(a!) kv_cache, "
         "Tensor slot_mapping) -> ()");
+  m.def("rope_and_cache(Tensor positions, Tensor(a!) q, Tensor(b!) k, "
+        "Tensor v, Tensor cos_sin_cache, int rot, Tensor(c!) kv_cache, "
+        "Tensor slot_mapping) -> ()");
   m.def("paged_decode_attention(Tensor(a!) out, Tensor q, Tensor kv_cache, "
         "Tensor block_table, Tensor seq_lens, float scale, int max_seq_len, "
         "int sliding_window, Tensor(b!) tmp_out, Tensor(c!) tmp_lse) -> ()");
@@ -135,6 +141,7 @@ TORCH_LIBRARY_IMPL(vllm_amd, CUDA, m) {
   m.impl("gelu_and_mul", &vllm_amd::gelu_and_mul);
   m.impl("rotary_embedding", &vllm_amd::rotary_embedding);
   m.impl("reshape_and_cache", &vllm_amd::reshape_and_cache);
+  m.impl("rope_and_cache", &vllm_amd::rope_and_cache);
   m.impl("paged_decode_attention", &vllm_amd::paged_decode_attention);
   m.impl("prefill_attention", &vllm_amd::prefill_attention);
   m.impl("lt_linear", &vllm_amd::lt_linear);

@@ -38,12 +38,17 @@ class Attention(nn.Module):
         self.kv_group = kv_group
 
     def forward(
-        self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
+        self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+        rope=None,
     ) -> torch.Tensor:
         """q: [T, Hq, D] or [T, Hq*D]; k/v likewise -> [T, Hq*D].
 
         Inputs may be strided head-slices of the fused QKV projection —
         the HIP kernels take row strides, so no contiguity copies here.
+
+        rope: optional (positions, RotaryEmbedding). When given, q and k
+        arrive un-rotated and are rotated here, in the same kernel that
+        writes K/V into the cache.
         """
         ctx = get_forward_context()
         meta = ctx.attn_metadata
@@ -59,6 +64,8 @@ class Attention(nn.Module):
             # Memory-profiling run: no cache allocated; compute attention
             # over just the new tokens (worst-case activation footprint is
             # what matters, not values).
+            if rope is not None:
+                rope[1](rope[0], q, k)
             return self._profile_attention(q, k, v, meta).reshape(T, -1)
 
         kv_cache = ctx.kv_caches[self.layer_idx]
@@ -66,7 +73,20 @@ class Attention(nn.Module):
                  and meta.block_table_w is not None)
         slot_mapping = meta.slot_mapping_w if use_w else meta.slot_mapping
         block_table = meta.block_table_w if use_w else meta.block_table
-        ops.reshape_and_cache(k, v, kv_cache, slot_mapping)
+        if rope is None:
+            ops.reshape_and_cache(k, v, kv_cache, slot_mapping)
+        else:
+            positions, rotary = rope
+            # The fused kernel gives each lane 8-dim chunks of both rotary
+            # halves; other geometries keep the two separate kernels.
+            if (rotary.is_neox and rotary.rotary_dim % 16 == 0
+                    and self.head_dim in (64, 128, 256)):
+                ops.rope_and_cache(
+                    positions, q, k, v, rotary.cos_sin_cache,
+                    rotary.rotary_dim, kv_cache, slot_mapping)
+            else:
+                rotary(positions, q, k)
+                ops.reshape_and_cache(k, v, kv_cache, slot_mapping)
         out = ops.attention_unified(
             q,
             kv_cache,

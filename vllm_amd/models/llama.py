@@ -131,8 +131,8 @@ class LlamaAttention(nn.Module):
                 q.reshape(-1, self.head_dim).contiguous()).view(q.shape)
             k = self.k_norm(
                 k.reshape(-1, self.head_dim).contiguous()).view(k.shape)
-        self.rotary_emb(positions, q, k)
-        out = self.attn(q, k, v)
+        # RoPE runs inside the attention layer, fused with the cache write.
+        out = self.attn(q, k, v, rope=(positions, self.rotary_emb))
         return self.o_proj(out, reduce_results=reduce_results)
 
 

@@ -79,6 +79,16 @@ def reshape_and_cache(key, value, kv_cache, slot_mapping):
     )
 
 
+def rope_and_cache(positions, q, k, v, cos_sin_cache, rotary_dim, kv_cache,
+                   slot_mapping, is_neox=True):
+    """apply_rope(q, k) in place plus reshape_and_cache(k, v): one kernel
+    on GPU, the two-call composition on CPU."""
+    return get_backend(q.device).rope_and_cache(
+        positions, q, k, v, cos_sin_cache, rotary_dim, kv_cache,
+        slot_mapping, is_neox
+    )
+
+
 def attention_unified(
     q,
     kv_cache,

@@ -84,6 +84,14 @@ def reshape_and_cache(key, value, kv_cache, slot_mapping):
     kv_cache[1, block_ids, :, offsets] = value.to(kv_cache.dtype)
 
 
+def rope_and_cache(positions, q, k, v, cos_sin_cache, rotary_dim, kv_cache,
+                   slot_mapping, is_neox=True):
+    """apply_rope(q, k) in place, then reshape_and_cache(k, v)."""
+    apply_rope(positions, q, k, cos_sin_cache, rotary_dim, is_neox)
+    reshape_and_cache(k, v, kv_cache, slot_mapping)
+    return q, k
+
+
 def _gather_kv(kv_cache, block_table_row, ctx_len):
     """Gather [ctx_len, Hkv, D] K and V for one request from paged cache."""
     block_size = kv_cache.shape[3]

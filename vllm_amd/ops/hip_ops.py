@@ -92,6 +92,15 @@ def reshape_and_cache(key, value, kv_cache, slot_mapping):
     _C.reshape_and_cache(key, value, kv_cache, slot_mapping)
 
 
+def rope_and_cache(positions, q, k, v, cos_sin_cache, rotary_dim, kv_cache,
+                   slot_mapping, is_neox=True):
+    # One launch for apply_rope + reshape_and_cache (csrc/elementwise.hip).
+    assert is_neox, "HIP rope kernel implements neox style"
+    _C.rope_and_cache(positions, q, k, v, cos_sin_cache, rotary_dim,
+                      kv_cache, slot_mapping)
+    return q, k
+
+
 def attention_unified(
     q,
     kv_cache,
