@@ -24,6 +24,7 @@ SOURCES = [
     CSRC / "elementwise.hip",
     CSRC / "comms.hip",
     CSRC / "moe.hip",
+    CSRC / "moe_w4a16.hip",
     CSRC / "mla.hip",
     CSRC / "quant_fp8.hip",
     CSRC / "gemm_w4a16.hip",

@@ -1189,7 +1189,9 @@ class ModelConfig:
     # linears only; lm_head and MoE expert weights stay in model dtype.
     # "int4": W4A16 — 4-bit codes, bf16 scale + integer zero-point per
     # 128-wide K group (quantized after load), bf16 activations, native
-    # dequant-GEMM (csrc/gemm_w4a16.hip). Same module selection as fp8.
+    # dequant-GEMM (csrc/gemm_w4a16.hip). Dense linears as for fp8, plus
+    # MoE expert weights (grouped GEMM, csrc/moe_w4a16.hip) where the
+    # layer is silu, H and local I are multiples of 128 and EPLB is off.
     quantization: Optional[str] = None
     spec: ModelSpec = None  # type: ignore[assignment]
 

@@ -207,10 +207,42 @@ class FusedMoE(nn.Module):
         self.slot_of.copy_(torch.tensor(slot_list, dtype=torch.int64))
         self.refresh_shuffled()
 
+    def quantize_int4(self) -> None:
+        """Convert the expert weights to packed 4-bit codes + per-group
+        scales/zero-points (registry.quantize_model_int4) and free the
+        wide copies. Only what the grouped W4A16 kernel serves is
+        quantized: silu experts with H and the local I multiples of 128.
+        EPLB moves the wide weights in place, so an EPLB layer stays in
+        model dtype."""
+        h, i = self.w2.shape[1], self.i_shard
+        if (self.activation != "silu" or h % 128 != 0 or i % 128 != 0
+                or self.eplb_window != 0):
+            return
+        for name in ("w13", "w2"):
+            w = getattr(self, name)
+            q, s, z = ops.quantize_experts_int4(w.data)
+            self.register_buffer(name + "_int4", q)
+            self.register_buffer(name + "_scale", s)
+            self.register_buffer(name + "_zero", z)
+            w.data = w.data.new_empty(0)
+
+    def _experts(self, hidden, topk_weights, topk_ids) -> torch.Tensor:
+        if getattr(self, "w13_int4", None) is not None:
+            return ops.fused_moe_int4(
+                hidden, self.w13_int4, self.w13_scale, self.w13_zero,
+                self.w2_int4, self.w2_scale, self.w2_zero, topk_weights,
+                topk_ids)
+        w13s, w2s = self._maybe_shuffled(hidden)
+        return ops.fused_moe(
+            hidden, self.w13, self.w2, topk_weights, topk_ids,
+            activation=self.activation, w13_shuf=w13s, w2_shuf=w2s,
+        )
+
     def refresh_shuffled(self) -> None:
         """Call after in-place weight updates (RL update_weights):
         re-shuffles INTO THE EXISTING storage so captured hipGraphs that
-        reference the fragment-major tensors stay valid."""
+        reference the fragment-major tensors stay valid. Nothing to do
+        for an int4 layer."""
         if self._w13_shuf is None:
             return
         from vllm_amd.ops import get_backend
@@ -271,20 +303,12 @@ class FusedMoE(nn.Module):
                 return torch.zeros_like(hidden)
             sel_ids = slot_map[topk_ids[slot_tok, slot_k]].unsqueeze(1)
             sel_w = topk_weights[slot_tok, slot_k].unsqueeze(1)
-            w13s, w2s = self._maybe_shuffled(hidden)
-            y = ops.fused_moe(
-                hidden[slot_tok], self.w13, self.w2, sel_w, sel_ids,
-                activation=self.activation, w13_shuf=w13s, w2_shuf=w2s,
-            )
+            y = self._experts(hidden[slot_tok], sel_w, sel_ids)
             out = torch.zeros(hidden.shape, dtype=torch.float32,
                               device=hidden.device)
             out.index_add_(0, slot_tok, y.float())
             return out.to(hidden.dtype)
-        w13s, w2s = self._maybe_shuffled(hidden)
-        return ops.fused_moe(
-            hidden, self.w13, self.w2, topk_weights, topk_ids,
-            activation=self.activation, w13_shuf=w13s, w2_shuf=w2s,
-        )
+        return self._experts(hidden, topk_weights, topk_ids)
 
     def load_full_weights(self, w1_full, w3_full, w2_full) -> None:
         """Shard full expert weights onto this rank: w1/w3 [E, I, H]

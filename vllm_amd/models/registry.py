@@ -176,11 +176,13 @@ def quantize_model_fp8(model: torch.nn.Module) -> None:
 
 
 def quantize_model_int4(model: torch.nn.Module) -> None:
-    """Quantize every dense linear to W4A16 after load and after TP
-    sharding (4-bit codes, bf16 scale + zero-point per 128-wide K group).
-    Same module selection as quantize_model_fp8: lm_head, embedding and
-    MoE experts stay in model dtype. A layer whose local shape the kernel
-    cannot tile (K % 128, N % 16) is left in model dtype."""
+    """Quantize every dense linear and every FusedMoE's expert weights to
+    W4A16 after load and after TP/EP sharding (4-bit codes, bf16 scale +
+    zero-point per 128-wide K group). lm_head and embedding stay in model
+    dtype. A layer whose local shape the kernels cannot tile (linear:
+    K % 128, N % 16; experts: H % 128, I % 128), a non-silu expert MLP
+    and an EPLB layer are left in model dtype."""
+    from vllm_amd.layers.fused_moe import FusedMoE
     from vllm_amd.layers.linear import (
         ColumnParallelLinear,
         ReplicatedLinear,
@@ -189,5 +191,5 @@ def quantize_model_int4(model: torch.nn.Module) -> None:
 
     for module in model.modules():
         if isinstance(module, (ColumnParallelLinear, RowParallelLinear,
-                               ReplicatedLinear)):
+                               ReplicatedLinear, FusedMoE)):
             module.quantize_int4()

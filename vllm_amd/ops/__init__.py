@@ -135,6 +135,7 @@ def quant_fp8_dynamic(x):
 # Weight quantization happens once at load — plain torch either device.
 from vllm_amd.ops._torch_ref import quantize_weight_fp8  # noqa: E402,F401
 from vllm_amd.ops._torch_ref import quantize_weight_int4  # noqa: E402,F401
+from vllm_amd.ops._torch_ref import quantize_experts_int4  # noqa: E402,F401
 
 
 def linear_int4(x, qweight, scales, zeros, bias=None):
@@ -142,6 +143,16 @@ def linear_int4(x, qweight, scales, zeros, bias=None):
     bf16 activations. Hand-written dequant-GEMM on GPU
     (csrc/gemm_w4a16.hip); dequantize + fp32 F.linear on CPU."""
     return get_backend(x.device).linear_int4(x, qweight, scales, zeros, bias)
+
+
+def fused_moe_int4(hidden, w13_q, w13_s, w13_z, w2_q, w2_s, w2_z,
+                   topk_weights, topk_ids):
+    """MoE expert MLP (silu) on 4-bit expert weights
+    (quantize_experts_int4). Grouped W4A16 dequant-GEMM on GPU
+    (csrc/moe_w4a16.hip); dequantize + fused_moe on CPU."""
+    return get_backend(hidden.device).fused_moe_int4(
+        hidden, w13_q, w13_s, w13_z, w2_q, w2_s, w2_z, topk_weights,
+        topk_ids)
 
 
 def concat_and_cache_mla(c_kv, k_pe, kv_cache, slot_mapping):

@@ -297,6 +297,25 @@ def fused_moe(hidden, w13, w2, topk_weights, topk_ids, activation="silu"):
     return out.to(hidden.dtype)
 
 
+def quantize_experts_int4(w):
+    """quantize_weight_int4 per expert: w [E, N, K] -> stacked (qweight
+    [E, N/16, K/128, 64, 4], scales, zeros [E, N/16, K/128, 16])."""
+    parts = [quantize_weight_int4(w[e]) for e in range(w.shape[0])]
+    return tuple(torch.stack(t) for t in zip(*parts))
+
+
+def fused_moe_int4(hidden, w13_q, w13_s, w13_z, w2_q, w2_s, w2_z,
+                   topk_weights, topk_ids):
+    """MoE on 4-bit expert weights, CPU path and ground truth: dequantize
+    every expert, then fused_moe (silu)."""
+    def dequant(q, s, z):
+        return torch.stack([dequantize_weight_int4(q[e], s[e], z[e])
+                            for e in range(q.shape[0])]).to(hidden.dtype)
+
+    return fused_moe(hidden, dequant(w13_q, w13_s, w13_z),
+                     dequant(w2_q, w2_s, w2_z), topk_weights, topk_ids)
+
+
 def concat_and_cache_mla(c_kv, k_pe, kv_cache, slot_mapping):
     """MLA cache write: c_kv [T, lora], k_pe [T, rope] ->
     kv_cache [num_blocks, block_size, lora+rope]."""

@@ -193,6 +193,7 @@ from vllm_amd.ops import _torch_ref  # noqa: E402
 from vllm_amd.ops._torch_ref import (  # noqa: E402,F401
     concat_and_cache_mla,
     grouped_topk,
+    quantize_experts_int4,
     topk_softmax,
 )
 
@@ -273,6 +274,24 @@ def moe_shuffle_weights(w):
     return v.reshape(E, (N // 16) * (K // 32) * 512).contiguous()
 
 
+def _moe_align(topk_ids, E, dev):
+    """On-device token->expert sort into BM-row tiles (moe_align). The
+    sizes depend only on (T, k, E), so there is no host sync. Returns
+    (em_max, sorted_ids, expert_tiles, inv_perm)."""
+    total = topk_ids.numel()
+    em_max = -(-(total + E * (_MOE_BM - 1)) // _MOE_BM) * _MOE_BM
+    ids32 = topk_ids.to(torch.int32).contiguous()
+    sorted_ids = torch.empty(em_max, dtype=torch.int32, device=dev)
+    expert_tiles = torch.empty(em_max // _MOE_BM, dtype=torch.int32,
+                               device=dev)
+    inv_perm = torch.empty(total, dtype=torch.int32, device=dev)
+    scratch = torch.empty(3 * E, dtype=torch.int32, device=dev)
+    counts, fill, off = scratch[:E], scratch[E:2 * E], scratch[2 * E:]
+    _C.moe_align(ids32, E, sorted_ids, expert_tiles, inv_perm, counts,
+                 fill, off)
+    return em_max, sorted_ids, expert_tiles, inv_perm
+
+
 def fused_moe_hip(hidden, w13, w2, topk_weights, topk_ids,
                   w13_shuf=None, w2_shuf=None):
     """Grouped-GEMM MFMA MoE (csrc/moe.hip): on-device token->expert
@@ -286,16 +305,7 @@ def fused_moe_hip(hidden, w13, w2, topk_weights, topk_ids,
     k = topk_ids.shape[1]
     total = T * k
     dev = hidden.device
-    em_max = -(-(total + E * (_MOE_BM - 1)) // _MOE_BM) * _MOE_BM
-    ids32 = topk_ids.to(torch.int32).contiguous()
-    sorted_ids = torch.empty(em_max, dtype=torch.int32, device=dev)
-    expert_tiles = torch.empty(em_max // _MOE_BM, dtype=torch.int32,
-                               device=dev)
-    inv_perm = torch.empty(total, dtype=torch.int32, device=dev)
-    scratch = torch.empty(3 * E, dtype=torch.int32, device=dev)
-    counts, fill, off = scratch[:E], scratch[E:2 * E], scratch[2 * E:]
-    _C.moe_align(ids32, E, sorted_ids, expert_tiles, inv_perm, counts,
-                 fill, off)
+    em_max, sorted_ids, expert_tiles, inv_perm = _moe_align(topk_ids, E, dev)
     y = torch.empty(em_max, twoI, dtype=hidden.dtype, device=dev)
     if w13_shuf is not None:
         _C.moe_gemm_shuf(hidden, w13_shuf, y, sorted_ids, expert_tiles,
@@ -309,6 +319,32 @@ def fused_moe_hip(hidden, w13, w2, topk_weights, topk_ids,
                          H, I, 0, total)
     else:
         _C.moe_gemm(act, w2, y2, sorted_ids, expert_tiles, 0, total)
+    out = torch.empty(T, H, dtype=hidden.dtype, device=dev)
+    _C.moe_combine(out, y2, topk_weights.float().contiguous(), inv_perm)
+    return out
+
+
+def fused_moe_int4(hidden, w13_q, w13_s, w13_z, w2_q, w2_s, w2_z,
+                   topk_weights, topk_ids):
+    """MoE expert MLP on 4-bit expert weights (csrc/moe_w4a16.hip): the
+    same align / silu_and_mul / combine as fused_moe_hip around the
+    grouped W4A16 dequant-GEMM. w*_q: int32 [E, N/16, K/128, 64, 4],
+    w*_s / w*_z: [E, N/16, K/128, 16]. bf16, silu; no host sync."""
+    T, H = hidden.shape
+    E = w13_q.shape[0]
+    twoI = w13_q.shape[1] * 16
+    k = topk_ids.shape[1]
+    total = T * k
+    dev = hidden.device
+    hidden = hidden.contiguous()
+    em_max, sorted_ids, expert_tiles, inv_perm = _moe_align(topk_ids, E, dev)
+    y = torch.empty(em_max, twoI, dtype=hidden.dtype, device=dev)
+    _C.moe_gemm_w4a16(hidden, w13_q, w13_s, w13_z, y, sorted_ids,
+                      expert_tiles, k, total)
+    act = silu_and_mul(y)
+    y2 = torch.empty(em_max, H, dtype=hidden.dtype, device=dev)
+    _C.moe_gemm_w4a16(act, w2_q, w2_s, w2_z, y2, sorted_ids, expert_tiles,
+                      0, total)
     out = torch.empty(T, H, dtype=hidden.dtype, device=dev)
     _C.moe_combine(out, y2, topk_weights.float().contiguous(), inv_perm)
     return out
