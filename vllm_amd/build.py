@@ -26,6 +26,7 @@ SOURCES = [
     CSRC / "moe.hip",
     CSRC / "moe_w4a16.hip",
     CSRC / "mla.hip",
+    CSRC / "mla_prefill.hip",
     CSRC / "quant_fp8.hip",
     CSRC / "gemm_w4a16.hip",
     CSRC / "attention_decode.hip",

@@ -66,6 +66,10 @@ void mla_decode(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
                 torch::Tensor kv_cache, torch::Tensor block_table,
                 torch::Tensor seq_lens, double scale, int64_t max_seq_len,
                 torch::Tensor tmp_out, torch::Tensor tmp_lse);
+void mla_prefill(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
+                 torch::Tensor kv_cache, torch::Tensor block_table,
+                 torch::Tensor query_start_loc, torch::Tensor seq_lens,
+                 double scale, int64_t num_decodes, int64_t max_query_len);
 torch::Tensor car_init(int64_t rank, int64_t world, int64_t max_bytes);
 void car_connect(torch::Tensor handles);
 bool car_is_ready();
@@ -123,6 +127,10 @@ TORCH_LIBRARY(vllm_amd, m) {
         "Tensor kv_cache, Tensor block_table, Tensor seq_lens, "
         "float scale, int max_seq_len, Tensor(b!) tmp_out, "
         "Tensor(c!) tmp_lse) -> ()");
+  m.def("mla_prefill(Tensor(a!) out, Tensor q_nope, Tensor q_pe, "
+        "Tensor kv_cache, Tensor block_table, Tensor query_start_loc, "
+        "Tensor seq_lens, float scale, int num_decodes, "
+        "int max_query_len) -> ()");
   // Custom xGMI collectives (comms.hip). init/connect/destroy are
   // host-side control ops and live on the catch-all dispatch below.
   m.def("car_init(int rank, int world, int max_bytes) -> Tensor");
@@ -166,4 +174,5 @@ TORCH_LIBRARY_IMPL(vllm_amd, CUDA, m) {
   m.impl("moe_gemm_w4a16", &vllm_amd::moe_gemm_w4a16);
   m.impl("moe_combine", &vllm_amd::moe_combine);
   m.impl("mla_decode", &vllm_amd::mla_decode);
+  m.impl("mla_prefill", &vllm_amd::mla_prefill);
 }

@@ -162,12 +162,19 @@ def concat_and_cache_mla(c_kv, k_pe, kv_cache, slot_mapping):
 
 
 def mla_attention(q_nope, q_pe, kv_cache, block_table, query_start_loc,
-                  seq_lens, scale, num_decodes=0, max_seq_len=0):
+                  seq_lens, scale, num_decodes=0, max_seq_len=0,
+                  max_query_len=0):
+    """Attention in the absorbed MLA space over the latent KV cache;
+    requests are ordered decodes-first. On GPU (lora 512 + rope 64,
+    bf16/fp16) decode rows run csrc/mla.hip and all other rows
+    csrc/mla_prefill.hip; max_seq_len/max_query_len are CPU-known hints
+    so that path never syncs."""
     backend = get_backend(q_nope.device)
     if backend is not _torch_ref:
         return backend.mla_attention(
             q_nope, q_pe, kv_cache, block_table, query_start_loc, seq_lens,
             scale, num_decodes=num_decodes, max_seq_len=max_seq_len,
+            max_query_len=max_query_len,
         )
     return backend.mla_attention(
         q_nope, q_pe, kv_cache, block_table, query_start_loc, seq_lens, scale

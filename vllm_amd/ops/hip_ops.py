@@ -201,11 +201,13 @@ _MLA_PART = 1024  # must match mla::PART in csrc/mla.hip
 
 
 def mla_decode(q_nope, q_pe, kv_cache, block_table, seq_lens, scale,
-               max_seq_len):
+               max_seq_len, out=None):
     """Absorbed-MQA MLA decode on the MFMA kernel (csrc/mla.hip);
     kv_lora_rank 512 + rope 64 latent cache."""
     T, Hq, lora = q_nope.shape
-    out = torch.empty(T, Hq, lora, dtype=q_nope.dtype, device=q_nope.device)
+    if out is None:
+        out = torch.empty(T, Hq, lora, dtype=q_nope.dtype,
+                          device=q_nope.device)
     if max_seq_len <= 0:
         max_seq_len = int(seq_lens.max().item())
     parts = max(1, -(-max_seq_len // _MLA_PART))
@@ -222,31 +224,50 @@ def mla_decode(q_nope, q_pe, kv_cache, block_table, seq_lens, scale,
     return out
 
 
+def mla_prefill(out, q_nope, q_pe, kv_cache, block_table, query_start_loc,
+                seq_lens, scale, num_decodes, max_query_len):
+    """MLA rows of requests [num_decodes, num_reqs) on the MFMA flash
+    kernel (csrc/mla_prefill.hip), written into out[T, Hq, 512] in place.
+    Causal, query token t of a request at position ctx - q_len + t."""
+    _C.mla_prefill(out, q_nope, q_pe, kv_cache, block_table,
+                   query_start_loc, seq_lens, scale, num_decodes,
+                   max_query_len)
+    return out
+
+
 def mla_attention(q_nope, q_pe, kv_cache, block_table, query_start_loc,
-                  seq_lens, scale, num_decodes=0, max_seq_len=0):
-    """Decode rows (query_len==1, first num_decodes) on the HIP MFMA
-    kernel; prefill rows on the torch composition (MLA prefill runs per
-    scheduler chunk — a bounded, non-steady-state path)."""
-    T = q_nope.shape[0]
-    num_reqs = seq_lens.shape[0]
+                  seq_lens, scale, num_decodes=0, max_seq_len=0,
+                  max_query_len=0):
+    """Decode rows (query_len==1, first num_decodes) on the MFMA decode
+    kernel, every other row (prefill chunks, continuations, speculative
+    verification) on the MFMA prefill kernel, both into one output.
+    max_seq_len/max_query_len come from the scheduler (CPU); with both
+    given there is no host sync. Geometries or dtypes the kernels are not
+    written for (lora != 512, rope != 64, fp32, a cache dtype that differs
+    from q) take the torch composition."""
     use_hip = (q_nope.shape[2] == 512 and q_pe.shape[2] == 64
                and q_nope.dtype in (torch.bfloat16, torch.float16)
                and kv_cache.dtype == q_nope.dtype)
-    if num_decodes > 0 and use_hip:
-        out_dec = mla_decode(
-            q_nope[:num_decodes].contiguous(),
-            q_pe[:num_decodes].contiguous(), kv_cache,
-            block_table, seq_lens[:num_decodes], scale, max_seq_len)
-        if num_decodes == T:
-            return out_dec
-        qsl = query_start_loc[num_decodes:] - num_decodes
-        out_pre = _torch_ref.mla_attention(
-            q_nope[num_decodes:], q_pe[num_decodes:], kv_cache,
-            block_table[num_decodes:], qsl, seq_lens[num_decodes:], scale)
-        return torch.cat([out_dec, out_pre], dim=0)
-    return _torch_ref.mla_attention(
-        q_nope, q_pe, kv_cache, block_table, query_start_loc, seq_lens,
-        scale)
+    if not use_hip:
+        return _torch_ref.mla_attention(
+            q_nope, q_pe, kv_cache, block_table, query_start_loc, seq_lens,
+            scale)
+    num_reqs = seq_lens.shape[0]
+    q_nope = q_nope.contiguous()
+    q_pe = q_pe.contiguous()
+    out = torch.empty_like(q_nope)
+    if num_decodes > 0:
+        mla_decode(q_nope[:num_decodes], q_pe[:num_decodes], kv_cache,
+                   block_table, seq_lens[:num_decodes], scale, max_seq_len,
+                   out=out[:num_decodes])
+    if num_decodes < num_reqs:
+        if max_query_len <= 0:
+            qsl = query_start_loc
+            max_query_len = int((qsl[1:] - qsl[:-1]).max().item())
+        mla_prefill(out, q_nope, q_pe, kv_cache, block_table,
+                    query_start_loc, seq_lens, scale, num_decodes,
+                    max_query_len)
+    return out
 
 
 _MOE_BM = 64  # must match moe::BM in csrc/moe.hip
