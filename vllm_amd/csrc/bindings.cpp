@@ -62,6 +62,8 @@ void moe_gemm_w4a16(torch::Tensor a, torch::Tensor qweight,
                     torch::Tensor c, torch::Tensor sorted,
                     torch::Tensor expert_tiles, int64_t topk_div,
                     int64_t total_flat);
+void concat_and_cache_mla(torch::Tensor c_kv, torch::Tensor k_pe,
+                          torch::Tensor kv_cache, torch::Tensor slot_mapping);
 void mla_decode(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
                 torch::Tensor kv_cache, torch::Tensor block_table,
                 torch::Tensor seq_lens, double scale, int64_t max_seq_len,
@@ -123,6 +125,8 @@ TORCH_LIBRARY(vllm_amd, m) {
   m.def("moe_gemm_w4a16(Tensor a, Tensor qweight, Tensor scales, "
         "Tensor zeros, Tensor(a!) c, Tensor sorted, Tensor expert_tiles, "
         "int topk_div, int total_flat) -> ()");
+  m.def("concat_and_cache_mla(Tensor c_kv, Tensor k_pe, "
+        "Tensor(a!) kv_cache, Tensor slot_mapping) -> ()");
   m.def("mla_decode(Tensor(a!) out, Tensor q_nope, Tensor q_pe, "
         "Tensor kv_cache, Tensor block_table, Tensor seq_lens, "
         "float scale, int max_seq_len, Tensor(b!) tmp_out, "
@@ -173,6 +177,7 @@ TORCH_LIBRARY_IMPL(vllm_amd, CUDA, m) {
   m.impl("moe_gemm_shuf", &vllm_amd::moe_gemm_shuf);
   m.impl("moe_gemm_w4a16", &vllm_amd::moe_gemm_w4a16);
   m.impl("moe_combine", &vllm_amd::moe_combine);
+  m.impl("concat_and_cache_mla", &vllm_amd::concat_and_cache_mla);
   m.impl("mla_decode", &vllm_amd::mla_decode);
   m.impl("mla_prefill", &vllm_amd::mla_prefill);
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #define WAVE_SIZE 64
 
@@ -76,15 +77,28 @@ DEVINL float fp8_e4m3_to_f32(uint8_t v) {
   return __builtin_amdgcn_cvt_f32_fp8((uint32_t)v, 0);
 }
 
-DEVINL uint8_t f32_to_fp8_e4m3(float f) {
+// Saturate finite values to +-448 (max finite e4m3); NaN propagates
+// through the hardware convert (same recipe as amd_hip_fp8.h).
+DEVINL float fp8_e4m3_saturate(float f) {
   union { float f; uint32_t u; } c;
   c.f = f;
-  // Saturate finite values to +-448 (max finite e4m3); NaN propagates
-  // through the hardware convert (same recipe as amd_hip_fp8.h).
-  float cl = f;
   if ((c.u & 0x7F800000u) != 0x7F800000u)
-    cl = __builtin_amdgcn_fmed3f(f, 448.f, -448.f);
+    return __builtin_amdgcn_fmed3f(f, 448.f, -448.f);
+  return f;
+}
+
+DEVINL uint8_t f32_to_fp8_e4m3(float f) {
+  const float cl = fp8_e4m3_saturate(f);
   return (uint8_t)__builtin_amdgcn_cvt_pk_fp8_f32(cl, cl, 0, false);
+}
+
+// Four floats -> one dword of e4m3 (byte j = element j), two packed converts.
+DEVINL uint32_t f32x4_to_fp8x4_e4m3(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_e4m3_saturate(a),
+                                          fp8_e4m3_saturate(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_e4m3_saturate(c),
+                                      fp8_e4m3_saturate(d), w, true);
+  return (uint32_t)w;
 }
 
 // Packed pair converts for vectorized cache reads: 2 elements/instr.
@@ -116,6 +130,40 @@ template <> struct CacheTraits<FP8CacheTag> {
   static DEVINL float get(vec8 v, int j) { return fp8_e4m3_to_f32(v[j]); }
   static DEVINL elem put(float f) { return f32_to_fp8_e4m3(f); }
 };
+
+// e4m3 -> bf16/fp16 is exact (4 exponent bits, 3 mantissa bits, smallest
+// subnormal 2^-9), so a cache row dequantised this way holds exactly the
+// values the fp8 cache stores. One packed convert per pair, then a pack:
+// the high halves of the two floats for bf16, v_cvt_pkrtz for fp16.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <typename Tag, bool HI>
+DEVINL uint32_t fp8x2_e4m3_to_pk16(uint32_t w) {
+  const f32x2 f = __builtin_amdgcn_cvt_pk_f32_fp8(w, HI);
+  if constexpr (std::is_same_v<Tag, BF16Tag>) {
+    return __builtin_amdgcn_perm(__float_as_uint(f[1]), __float_as_uint(f[0]),
+                                 0x07060302u);
+  } else {
+    return __builtin_bit_cast(uint32_t,
+                              __builtin_amdgcn_cvt_pkrtz(f[0], f[1]));
+  }
+}
+
+// 8 cache elements -> 8 compute-dtype elements (identity for a 16-bit cache).
+template <typename Tag, typename CTag>
+DEVINL s16x8 cache_vec8_to_16(typename CacheTraits<CTag>::vec8 v) {
+  if constexpr (std::is_same_v<CTag, FP8CacheTag>) {
+    const u32x2 w = __builtin_bit_cast(u32x2, v);
+    const u32x4 r = {fp8x2_e4m3_to_pk16<Tag, false>(w[0]),
+                     fp8x2_e4m3_to_pk16<Tag, true>(w[0]),
+                     fp8x2_e4m3_to_pk16<Tag, false>(w[1]),
+                     fp8x2_e4m3_to_pk16<Tag, true>(w[1])};
+    return __builtin_bit_cast(s16x8, r);
+  } else {
+    return v;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Wave reductions (64 lanes).

@@ -23,6 +23,11 @@
 // Grid (num_decodes, num_parts, ceil(Hq/32)); partitions of 1024 tokens
 // produce fp32 partials + (m, l) merged by mla_reduce_kernel — same
 // flash-partition scheme as the GQA decode kernel.
+//
+// The latent cache is the compute dtype or e4m3 (kv_cache_dtype="fp8",
+// 576 B per token): mla_decode_kernel<Tag, CTag> dequantises while
+// staging, and concat_and_cache_mla_kernel below is the cache write for
+// both. Measurements: profiles/mla_fp8_cache.md.
 
 #include <torch/all.h>
 #include <c10/hip/HIPStream.h>
@@ -45,12 +50,16 @@ constexpr float NEG_INF = -1e30f;
 
 DEVINL int swz(int row, int byte_off) { return byte_off ^ ((row & 7) << 4); }
 
-template <typename Tag>
+// CTag is the cache element: the compute dtype, or FP8CacheTag for an
+// e4m3 latent cache (576 B per token). Only staging differs: the fp8
+// subtile is dequantised (exactly) on its way into the same LDS images.
+template <typename Tag, typename CTag>
 __launch_bounds__(THREADS) __global__
 void mla_decode_kernel(short* __restrict__ out,           // [T, Hq, LORA]
                        const short* __restrict__ q_nope,  // [T, Hq, LORA]
                        const short* __restrict__ q_pe,    // [T, Hq, ROPE]
-                       const short* __restrict__ kv,      // [NB, BS, DK]
+                       const typename CacheTraits<CTag>::elem* __restrict__
+                           kv,                            // [NB, BS, DK]
                        const int* __restrict__ block_table, int bt_stride,
                        const int* __restrict__ seq_lens, float scale,
                        int num_heads, int block_size,
@@ -120,8 +129,48 @@ void mla_decode_kernel(short* __restrict__ out,           // [T, Hq, LORA]
   __syncthreads();
 
   for (int sub0 = t_begin; sub0 < t_end; sub0 += SUB) {
-    // ---- stage: 32 tokens x 1152B; 2304 16B chunks over 256 threads.
-    {
+    // ---- stage, fp8 cache: 32 tokens x 576B; 1152 16B chunks of 16
+    // latent values over 256 threads (4.5 rounds: the last is half full).
+    // All of a thread's loads are issued before the first convert.
+    if constexpr (std::is_same_v<CTag, FP8CacheTag>) {
+      constexpr int CPT = DK / 16;                            // 36 per token
+      constexpr int ROUNDS = (SUB * CPT + THREADS - 1) / THREADS;  // 5
+      u32x4 raw[ROUNDS];
+#pragma unroll
+      for (int it = 0; it < ROUNDS; ++it) {
+        const int c = tid + it * THREADS;
+        const int t_glob = sub0 + c / CPT;
+        raw[it] = u32x4{0u, 0u, 0u, 0u};
+        if (c < SUB * CPT && t_glob < t_end) {
+          const int blk = block_table[seq * bt_stride + t_glob / block_size];
+          raw[it] = *reinterpret_cast<const u32x4*>(
+              kv + ((long)blk * block_size + t_glob % block_size) * DK +
+              (c % CPT) * 16);
+        }
+      }
+#pragma unroll
+      for (int it = 0; it < ROUNDS; ++it) {
+        const int c = tid + it * THREADS;
+        if (c >= SUB * CPT) break;
+        const int tok = c / CPT;
+        const int f16 = c % CPT;  // 16-elem feature chunk
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const u32x2 w = {raw[it][half * 2], raw[it][half * 2 + 1]};
+          const s16x8 v =
+              cache_vec8_to_16<Tag, CTag>(__builtin_bit_cast(u8x8, w));
+          const int f8 = f16 * 2 + half;
+          *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(k_lds) +
+                                    tok * (DK * 2) + swz(tok, f8 * 16)) = v;
+          if (f8 * 8 < LORA) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              vt_lds[(f8 * 8 + j) * SUB + tok] = v[j];
+          }
+        }
+      }
+    } else {
+      // ---- stage: 32 tokens x 1152B; 2304 16B chunks over 256 threads.
       for (int c = tid; c < SUB * (DK / 8); c += THREADS) {
         const int tok = c / (DK / 8);
         const int f8 = c % (DK / 8);      // 8-elem feature chunk
@@ -307,7 +356,103 @@ __global__ void mla_reduce_kernel(short* __restrict__ out,
   }
 }
 
+// Cache write: row t of c_kv [T, lora] ++ k_pe [T, rope] goes to latent
+// cache row slot_mapping[t] of kv_cache [NB, BS, lora + rope]. A lane owns
+// one 8-element chunk: a 16 B load, then a 16 B copy (16-bit cache) or the
+// packed saturating e4m3 convert and an 8 B store. Chunks are numbered
+// token-major over the whole launch, so consecutive lanes store
+// consecutive chunks of one cache row and a 256-thread block carries as
+// many tokens as fit (3.5 at 72 chunks per token) instead of idling.
+// lora and rope are runtime multiples of 8; slot < 0 is a padding row.
+constexpr int CW_THREADS = 256;
+
+template <typename Tag, typename CTag>
+__launch_bounds__(CW_THREADS) __global__
+void concat_and_cache_mla_kernel(
+    const short* __restrict__ c_kv, const short* __restrict__ k_pe,
+    typename CacheTraits<CTag>::vec8* __restrict__ kv_cache,
+    const int64_t* __restrict__ slot_mapping, int64_t ckv_stride,
+    int64_t kpe_stride, int lora_chunks, int row_chunks, int64_t num_slots,
+    int64_t total_chunks) {
+  const int64_t g = (int64_t)blockIdx.x * CW_THREADS + threadIdx.x;
+  if (g >= total_chunks) return;
+  const int64_t t = g / row_chunks;
+  const int c = (int)(g % row_chunks);
+  const int64_t slot = slot_mapping[t];
+  if (slot < 0 || slot >= num_slots) return;
+  const short* src = c < lora_chunks
+                         ? c_kv + t * ckv_stride + c * 8
+                         : k_pe + t * kpe_stride + (c - lora_chunks) * 8;
+  const s16x8 v = *reinterpret_cast<const s16x8*>(src);
+  typename CacheTraits<CTag>::vec8* dst = kv_cache + slot * row_chunks + c;
+  if constexpr (std::is_same_v<CTag, FP8CacheTag>) {
+    const u32x2 w = {
+        f32x4_to_fp8x4_e4m3(to_f32<Tag>(v[0]), to_f32<Tag>(v[1]),
+                            to_f32<Tag>(v[2]), to_f32<Tag>(v[3])),
+        f32x4_to_fp8x4_e4m3(to_f32<Tag>(v[4]), to_f32<Tag>(v[5]),
+                            to_f32<Tag>(v[6]), to_f32<Tag>(v[7]))};
+    *dst = __builtin_bit_cast(u8x8, w);
+  } else {
+    *dst = v;
+  }
+}
+
 }  // namespace mla
+
+void concat_and_cache_mla(torch::Tensor c_kv, torch::Tensor k_pe,
+                          torch::Tensor kv_cache, torch::Tensor slot_mapping) {
+  using namespace mla;
+  TORCH_CHECK(c_kv.dim() == 2 && k_pe.dim() == 2 && kv_cache.dim() == 3,
+              "concat_and_cache_mla: c_kv [T, lora], k_pe [T, rope], "
+              "kv_cache [NB, BS, lora + rope]");
+  const int64_t T = c_kv.size(0);
+  const int64_t lora = c_kv.size(1);
+  const int64_t rope = k_pe.size(1);
+  TORCH_CHECK(k_pe.size(0) == T && slot_mapping.numel() == T,
+              "token counts differ");
+  TORCH_CHECK(lora % 8 == 0 && rope % 8 == 0 && lora + rope > 0 &&
+              kv_cache.size(2) == lora + rope,
+              "lora and rope must be multiples of 8 summing to the cache row");
+  const auto dt = c_kv.scalar_type();
+  TORCH_CHECK((dt == torch::kBFloat16 || dt == torch::kHalf) &&
+              k_pe.scalar_type() == dt, "c_kv/k_pe must both be bf16 or fp16");
+  const bool fp8c = kv_cache.scalar_type() == torch::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8c || kv_cache.scalar_type() == dt,
+              "kv_cache must be fp8 or the input dtype");
+  TORCH_CHECK(kv_cache.is_contiguous() && slot_mapping.is_contiguous() &&
+              slot_mapping.scalar_type() == torch::kInt64);
+  auto rows_16b = [](const torch::Tensor& x) {
+    return x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
+           reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(rows_16b(c_kv) && rows_16b(k_pe),
+              "c_kv/k_pe rows must be contiguous and 16B-aligned");
+  if (T == 0) return;
+  const int row_chunks = (int)((lora + rope) / 8);
+  const int64_t total = T * row_chunks;
+  const int64_t num_slots = kv_cache.size(0) * kv_cache.size(1);
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  auto launch = [&](auto tag, auto ctag) {
+    using Tag = decltype(tag);
+    using CTag = decltype(ctag);
+    hipLaunchKernelGGL(
+        (concat_and_cache_mla_kernel<Tag, CTag>),
+        dim3((unsigned)((total + CW_THREADS - 1) / CW_THREADS)),
+        dim3(CW_THREADS), 0, stream, (const short*)c_kv.data_ptr(),
+        (const short*)k_pe.data_ptr(),
+        (typename CacheTraits<CTag>::vec8*)kv_cache.data_ptr(),
+        slot_mapping.data_ptr<int64_t>(), c_kv.stride(0), k_pe.stride(0),
+        (int)(lora / 8), row_chunks, num_slots, total);
+  };
+  if (dt == torch::kBFloat16) {
+    if (fp8c) launch(BF16Tag{}, FP8CacheTag{});
+    else      launch(BF16Tag{}, BF16Tag{});
+  } else {
+    if (fp8c) launch(FP16Tag{}, FP8CacheTag{});
+    else      launch(FP16Tag{}, FP16Tag{});
+  }
+  HIP_CHECK_KERNEL();
+}
 
 void mla_decode(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
                 torch::Tensor kv_cache, torch::Tensor block_table,
@@ -320,7 +465,13 @@ void mla_decode(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
   TORCH_CHECK(kv_cache.size(2) == DK);
   TORCH_CHECK(q_nope.is_contiguous() && q_pe.is_contiguous() &&
               out.is_contiguous() && kv_cache.is_contiguous());
-  TORCH_CHECK(out.scalar_type() == q_nope.scalar_type());
+  TORCH_CHECK(out.scalar_type() == q_nope.scalar_type() &&
+              q_pe.scalar_type() == q_nope.scalar_type());
+  // The kernel reads the cache as CTag elements: any other dtype would be
+  // read past its end.
+  const bool fp8c = kv_cache.scalar_type() == torch::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8c || kv_cache.scalar_type() == q_nope.scalar_type(),
+              "mla_decode: kv_cache must be fp8 or the q dtype");
   const int T = (int)q_nope.size(0);
   const int Hq = (int)q_nope.size(1);
   const int bs = (int)kv_cache.size(1);
@@ -330,12 +481,14 @@ void mla_decode(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
                 tmp_lse.numel() >= (long)T * Hq * parts * 2);
   auto stream = c10::hip::getCurrentHIPStream().stream();
   dim3 grid(T, parts, ceil_div(Hq, HG));
-  auto launch = [&](auto tag) {
+  auto launch = [&](auto tag, auto ctag) {
     using Tag = decltype(tag);
+    using CTag = decltype(ctag);
     hipLaunchKernelGGL(
-        (mla_decode_kernel<Tag>), grid, dim3(THREADS), 0, stream,
+        (mla_decode_kernel<Tag, CTag>), grid, dim3(THREADS), 0, stream,
         (short*)out.data_ptr(), (const short*)q_nope.data_ptr(),
-        (const short*)q_pe.data_ptr(), (const short*)kv_cache.data_ptr(),
+        (const short*)q_pe.data_ptr(),
+        (const typename CacheTraits<CTag>::elem*)kv_cache.data_ptr(),
         block_table.data_ptr<int>(), (int)block_table.size(1),
         seq_lens.data_ptr<int>(), (float)scale, Hq, bs,
         parts > 1 ? tmp_out.data_ptr<float>() : nullptr,
@@ -348,12 +501,15 @@ void mla_decode(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
                          seq_lens.data_ptr<int>(), Hq, parts);
     }
   };
-  if (q_nope.scalar_type() == torch::kBFloat16)
-    launch(BF16Tag{});
-  else if (q_nope.scalar_type() == torch::kHalf)
-    launch(FP16Tag{});
-  else
+  if (q_nope.scalar_type() == torch::kBFloat16) {
+    if (fp8c) launch(BF16Tag{}, FP8CacheTag{});
+    else      launch(BF16Tag{}, BF16Tag{});
+  } else if (q_nope.scalar_type() == torch::kHalf) {
+    if (fp8c) launch(FP16Tag{}, FP8CacheTag{});
+    else      launch(FP16Tag{}, FP16Tag{});
+  } else {
     TORCH_CHECK(false, "mla_decode: bf16/fp16 only");
+  }
   HIP_CHECK_KERNEL();
 }
 

@@ -33,7 +33,9 @@
 // loads are issued before the MFMA phase and land in registers while it
 // runs. The only block barriers are the two around staging.
 // 256 VGPRs + 216 AGPRs, no scratch, 73 KB LDS: one block per CU.
-// Measurements: profiles/mla_prefill.md.
+// Measurements: profiles/mla_prefill.md. With an e4m3 latent cache
+// (CTag = FP8CacheTag; 198 AGPRs) the prefetch holds raw fp8 and staging
+// dequantises: profiles/mla_fp8_cache.md.
 
 #include <torch/all.h>
 #include <c10/hip/HIPStream.h>
@@ -73,12 +75,16 @@ template <> DEVINL f32x4 mma<FP16Tag>(s16x8 a, s16x8 b, f32x4 c) {
       __builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
 }
 
-template <typename Tag>
+// CTag is the cache element: the compute dtype, or FP8CacheTag for an
+// e4m3 latent cache, whose prefetched subtile waits in registers as raw
+// fp8 (18 dwords, not 36) and is dequantised (exactly) on its way into LDS.
+template <typename Tag, typename CTag>
 __launch_bounds__(THREADS) __global__
 void mla_prefill_kernel(short* __restrict__ out,           // [T, Hq, LORA]
                         const short* __restrict__ q_nope,  // [T, Hq, LORA]
                         const short* __restrict__ q_pe,    // [T, Hq, ROPE]
-                        const short* __restrict__ kv,      // [NB, BS, DK]
+                        const typename CacheTraits<CTag>::elem* __restrict__
+                            kv,                            // [NB, BS, DK]
                         const int* __restrict__ block_table, int bt_stride,
                         const int* __restrict__ query_start_loc,
                         const int* __restrict__ seq_lens, float scale,
@@ -142,21 +148,22 @@ void mla_prefill_kernel(short* __restrict__ out,           // [T, Hq, LORA]
   // ---- staging helpers.
   const int s_tok = tid & (SUB - 1);
   const int s_f8 = tid / SUB;  // 0..7; chunk it covers features (s_f8+8it)*8
-  s16x8 pre[STAGE_IT];
+  using cvec = typename CacheTraits<CTag>::vec8;
+  cvec pre[STAGE_IT];
   auto load_subtile = [&](int sub0) {
     const int t_glob = sub0 + s_tok;
     if (t_glob < kv_end) {
       const int blk =
           block_table[(long)req * bt_stride + t_glob / block_size];
-      const short* src =
+      const typename CacheTraits<CTag>::elem* src =
           kv + ((long)blk * block_size + t_glob % block_size) * DK + s_f8 * 8;
 #pragma unroll
       for (int it = 0; it < STAGE_IT; ++it)
-        pre[it] = *reinterpret_cast<const s16x8*>(src + it * 64);
+        pre[it] = *reinterpret_cast<const cvec*>(src + it * 64);
     } else {
 #pragma unroll
       for (int it = 0; it < STAGE_IT; ++it)
-        pre[it] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        pre[it] = cvec{0, 0, 0, 0, 0, 0, 0, 0};
     }
   };
   // Transposed copy through the lane pair (tok, tok^1): each lane gets
@@ -170,11 +177,11 @@ void mla_prefill_kernel(short* __restrict__ out,           // [T, Hq, LORA]
 #pragma unroll
     for (int it = 0; it < STAGE_IT; ++it) {
       const int f8 = s_f8 + it * 8;
+      const s16x8 v = cache_vec8_to_16<Tag, CTag>(pre[it]);
       *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(k_lds) +
-                                s_tok * (DK * 2) + swz(s_tok, f8 * 16)) =
-          pre[it];
+                                s_tok * (DK * 2) + swz(s_tok, f8 * 16)) = v;
       if (it < LORA / 64) {
-        const i32x4 w = __builtin_bit_cast(i32x4, pre[it]);
+        const i32x4 w = __builtin_bit_cast(i32x4, v);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
           // quad_perm(1,0,3,2): lane ^ 1.
@@ -311,8 +318,10 @@ void mla_prefill(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
               block_table.is_contiguous());
   TORCH_CHECK(out.sizes() == q_nope.sizes());
   TORCH_CHECK(out.scalar_type() == q_nope.scalar_type() &&
-              q_pe.scalar_type() == q_nope.scalar_type() &&
-              kv_cache.scalar_type() == q_nope.scalar_type());
+              q_pe.scalar_type() == q_nope.scalar_type());
+  const bool fp8c = kv_cache.scalar_type() == torch::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8c || kv_cache.scalar_type() == q_nope.scalar_type(),
+              "mla_prefill: kv_cache must be fp8 or the q dtype");
   const int num_reqs = (int)seq_lens.size(0);
   TORCH_CHECK(query_start_loc.numel() == num_reqs + 1 &&
               block_table.size(0) >= num_reqs);
@@ -323,22 +332,27 @@ void mla_prefill(torch::Tensor out, torch::Tensor q_nope, torch::Tensor q_pe,
   const int bs = (int)kv_cache.size(1);
   auto stream = c10::hip::getCurrentHIPStream().stream();
   dim3 grid(ceil_div((int)max_query_len * Hq, ROWS), num_prefills);
-  auto launch = [&](auto tag) {
+  auto launch = [&](auto tag, auto ctag) {
     using Tag = decltype(tag);
+    using CTag = decltype(ctag);
     hipLaunchKernelGGL(
-        (mla_prefill_kernel<Tag>), grid, dim3(THREADS), 0, stream,
+        (mla_prefill_kernel<Tag, CTag>), grid, dim3(THREADS), 0, stream,
         (short*)out.data_ptr(), (const short*)q_nope.data_ptr(),
-        (const short*)q_pe.data_ptr(), (const short*)kv_cache.data_ptr(),
+        (const short*)q_pe.data_ptr(),
+        (const typename CacheTraits<CTag>::elem*)kv_cache.data_ptr(),
         block_table.data_ptr<int>(), (int)block_table.size(1),
         query_start_loc.data_ptr<int>(), seq_lens.data_ptr<int>(),
         (float)scale, Hq, bs, (int)num_decodes);
   };
-  if (q_nope.scalar_type() == torch::kBFloat16)
-    launch(BF16Tag{});
-  else if (q_nope.scalar_type() == torch::kHalf)
-    launch(FP16Tag{});
-  else
+  if (q_nope.scalar_type() == torch::kBFloat16) {
+    if (fp8c) launch(BF16Tag{}, FP8CacheTag{});
+    else      launch(BF16Tag{}, BF16Tag{});
+  } else if (q_nope.scalar_type() == torch::kHalf) {
+    if (fp8c) launch(FP16Tag{}, FP8CacheTag{});
+    else      launch(FP16Tag{}, FP16Tag{});
+  } else {
     TORCH_CHECK(false, "mla_prefill: bf16/fp16 only");
+  }
   HIP_CHECK_KERNEL();
 }
 

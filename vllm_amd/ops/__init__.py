@@ -166,7 +166,8 @@ def mla_attention(q_nope, q_pe, kv_cache, block_table, query_start_loc,
                   max_query_len=0):
     """Attention in the absorbed MLA space over the latent KV cache;
     requests are ordered decodes-first. On GPU (lora 512 + rope 64,
-    bf16/fp16) decode rows run csrc/mla.hip and all other rows
+    bf16/fp16, cache of that dtype or e4m3) decode rows run csrc/mla.hip
+    and all other rows
     csrc/mla_prefill.hip; max_seq_len/max_query_len are CPU-known hints
     so that path never syncs."""
     backend = get_backend(q_nope.device)

@@ -318,13 +318,16 @@ def fused_moe_int4(hidden, w13_q, w13_s, w13_z, w2_q, w2_s, w2_z,
 
 def concat_and_cache_mla(c_kv, k_pe, kv_cache, slot_mapping):
     """MLA cache write: c_kv [T, lora], k_pe [T, rope] ->
-    kv_cache [num_blocks, block_size, lora+rope]."""
+    kv_cache [num_blocks, block_size, lora+rope]. An fp8 (e4m3) cache
+    saturates at +-448: a bare cast would turn larger values into NaN."""
     block_size = kv_cache.shape[1]
     blk = slot_mapping // block_size
     off = slot_mapping % block_size
     lora = c_kv.shape[1]
-    kv_cache[blk, off, :lora] = c_kv
-    kv_cache[blk, off, lora:] = k_pe
+    if kv_cache.dtype == torch.float8_e4m3fn:
+        c_kv, k_pe = c_kv.clamp(-448.0, 448.0), k_pe.clamp(-448.0, 448.0)
+    kv_cache[blk, off, :lora] = c_kv.to(kv_cache.dtype)
+    kv_cache[blk, off, lora:] = k_pe.to(kv_cache.dtype)
 
 
 def mla_attention(

@@ -191,13 +191,31 @@ def _warn_prefill_fallback(head_dim: int) -> None:
 # MoE routing (small [T, E] tensors — torch ops are fine here).
 from vllm_amd.ops import _torch_ref  # noqa: E402
 from vllm_amd.ops._torch_ref import (  # noqa: E402,F401
-    concat_and_cache_mla,
     grouped_topk,
     quantize_experts_int4,
     topk_softmax,
 )
 
 _MLA_PART = 1024  # must match mla::PART in csrc/mla.hip
+
+
+def concat_and_cache_mla(c_kv, k_pe, kv_cache, slot_mapping):
+    """MLA cache write (csrc/mla.hip): bf16/fp16 rows into a cache of the
+    same dtype (a copy) or an e4m3 cache (saturating convert); rows with
+    slot < 0 are skipped. Other dtypes keep the torch function."""
+    if (c_kv.dtype not in (torch.bfloat16, torch.float16)
+            or k_pe.dtype != c_kv.dtype
+            or kv_cache.dtype not in (c_kv.dtype, torch.float8_e4m3fn)):
+        return _torch_ref.concat_and_cache_mla(c_kv, k_pe, kv_cache,
+                                               slot_mapping)
+
+    def rows_16b(x):  # the kernel loads 16 B chunks of a row
+        ok = (x.stride(1) == 1 and x.stride(0) % 8 == 0
+              and x.data_ptr() % 16 == 0)
+        return x if ok else x.contiguous()
+
+    _C.concat_and_cache_mla(rows_16b(c_kv), rows_16b(k_pe), kv_cache,
+                            slot_mapping)
 
 
 def mla_decode(q_nope, q_pe, kv_cache, block_table, seq_lens, scale,
@@ -242,12 +260,13 @@ def mla_attention(q_nope, q_pe, kv_cache, block_table, query_start_loc,
     kernel, every other row (prefill chunks, continuations, speculative
     verification) on the MFMA prefill kernel, both into one output.
     max_seq_len/max_query_len come from the scheduler (CPU); with both
-    given there is no host sync. Geometries or dtypes the kernels are not
-    written for (lora != 512, rope != 64, fp32, a cache dtype that differs
-    from q) take the torch composition."""
+    given there is no host sync. The cache is q's dtype or e4m3
+    (kv_cache_dtype="fp8"). Geometries or dtypes the kernels are not
+    written for (lora != 512, rope != 64, fp32, any other cache dtype)
+    take the torch composition."""
     use_hip = (q_nope.shape[2] == 512 and q_pe.shape[2] == 64
                and q_nope.dtype in (torch.bfloat16, torch.float16)
-               and kv_cache.dtype == q_nope.dtype)
+               and kv_cache.dtype in (q_nope.dtype, torch.float8_e4m3fn))
     if not use_hip:
         return _torch_ref.mla_attention(
             q_nope, q_pe, kv_cache, block_table, query_start_loc, seq_lens,

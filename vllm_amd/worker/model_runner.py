@@ -488,11 +488,10 @@ class ModelRunner:
                 self.kv_caches = []
                 return
         if spec.is_mla:
-            # MLA cache stays at model precision (fp8 MLA cache later).
             per_tok = spec.kv_lora_rank + spec.qk_rope_head_dim
             self.kv_caches = [
                 torch.zeros(num_blocks, self.block_size, per_tok,
-                            dtype=self.dtype, device=self.device)
+                            dtype=self.cache_dtype, device=self.device)
                 for _ in range(self._num_local_layers())
             ]
             return
